@@ -6,7 +6,7 @@ HBM-resident page images: k_prologue -> (delta / byte-array walks) -> k_scan -> 
 PLAIN copies, booleans, dictionaries) / k_delta_* / k_ba_* / k_nest_*.
 Default workload = BASELINE.json configs[1] (C2): 100M rows x 6 columns, data page V2, 16 row
 groups, at EVERY N: each rank decodes its own C2 file ("scaling": "weak"), so the driver's N=1 and
-N>1 lines measure the same per-GPU work.  Every line also carries `c3_strong`, BASELINE.json
+N>1 lines measure the same per-GPU work.  With --full every line also carries `c3_strong`, BASELINE.json
 configs[2] (C3: ONE 1B-row file of 128 row groups): at N>1 the row groups are sharded in contiguous
 blocks over the N GPUs and timed as strong scaling; at N=1 the whole file is timed, and so is rank
 0's share of it at N = 2, 4, 8 (shard.row_group_block) on the one GPU -- the single-GPU proxy of the
@@ -14,7 +14,14 @@ blocks over the N GPUs and timed as strong scaling; at N=1 the whole file is tim
 line.)  One process per GPU, no data-path collective: the only collectives are the measurement
 reductions and one all-gather of the blocks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5|c5z] [--rows R] [--no-c3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5|c5z] [--rows R]
+                  [--dump-outputs DIR] [--full [--no-c3] ...]
+
+A plain run does what the headline figure needs: it builds the file, loads it, warms up, times the
+K steps and prints the line (`kernels`, `roofline` and every sub-record null).  --full adds the rest:
+the profiled passes (per-kernel table, roofline), the CPU baseline and its bit-exact check, the
+end-to-end passes, `next_row`, `c3_strong`, `c1_x10` and `mixed_1b` (each with its --no-* switch).
+--dump-outputs DIR writes what the last timed step decoded (dump_outputs) as DIR/<name>.npy.
 
 --gpus N without a launcher (WORLD_SIZE unset): bench.py starts the N rank processes itself (before
 anything touches the GPU), rendezvous at 127.0.0.1; under torchrun it is one of the ranks.
@@ -208,6 +215,81 @@ def check_statuses(batch, num_chunks, native, where):
         if o.status != native.OK:
             raise RuntimeError(f"{where}: chunk {c} failed: {native.STATUS.get(o.status, o.status)} "
                                f"page {o.error_page} phase {o.error_phase}")
+
+
+DUMP_BUDGET = 48 << 20  # bytes of array data --dump-outputs writes in all (with the .npy headers: under 64 MB)
+DUMP_BLOCK = 4096  # elements per sampled block
+DUMP_SEED = 2024
+
+
+def dump_outputs(ctx, batch, chunks, ncols, rg0, out_dir, prefix=""):
+    """--dump-outputs: what a caller of the timed path receives from the batch's LAST run, per chunk
+    (row group rg, column ci) as <out_dir>/<prefix>rg<rg>_c<ci>_<array>.npy:
+      values      the non-null values: FLOAT as float32, DOUBLE as float64, INT32 as float64, INT64 as
+                  its little-endian 32-bit words as float64 (two per value), every other type
+                  (BOOLEAN, INT96, FIXED_LEN_BYTE_ARRAY) one float32 per byte -- all exact
+      offsets, bytes          a BYTE_ARRAY chunk's int64 offsets (float64) and bytes (float32 each)
+      def_levels, rep_levels  one float32 per level
+      nest<k>_offsets, nest<k>_validity, leaf_validity   a repeated column's list structure
+    Every array gets an equal share of DUMP_BUDGET; a larger one is sampled in blocks of DUMP_BLOCK
+    elements at positions drawn from a generator seeded with DUMP_SEED and the array's name, so
+    two runs with the same arguments write the same elements.  Returns (files, bytes)."""
+    import zlib
+
+    import numpy as np
+
+    FLOAT, DOUBLE, INT32, INT64 = 4, 5, 1, 2  # parquet physical types (pqh_column.physical_type)
+    arrays = []  # (name, device pointer, elements, dtype read, dtype written)
+    for c, ch in enumerate(chunks):
+        o = batch.chunk_out(c)
+        name = f"{prefix}rg{rg0 + c // ncols:03d}_c{c % ncols:02d}_"
+        pt = ch.column.physical_type
+        if o.value_size > 0:
+            nb = o.num_non_null * o.value_size
+            if pt == FLOAT and o.value_size == 4:
+                arrays.append((name + "values", o.values, nb // 4, np.float32, np.float32))
+            elif pt == DOUBLE and o.value_size == 8:
+                arrays.append((name + "values", o.values, nb // 8, np.float64, np.float64))
+            elif pt == INT32 and o.value_size == 4:
+                arrays.append((name + "values", o.values, nb // 4, np.int32, np.float64))
+            elif pt == INT64 and o.value_size == 8:
+                arrays.append((name + "values", o.values, nb // 4, np.uint32, np.float64))
+            else:
+                arrays.append((name + "values", o.values, nb, np.uint8, np.float32))
+        else:
+            arrays.append((name + "offsets", o.offsets, o.num_non_null + 1, np.int64, np.float64))
+            arrays.append((name + "bytes", o.bytes, o.num_bytes, np.uint8, np.float32))
+        if o.def_levels:
+            arrays.append((name + "def_levels", o.def_levels, o.num_values, np.uint8, np.float32))
+        if o.rep_levels:
+            arrays.append((name + "rep_levels", o.rep_levels, o.num_values, np.uint8, np.float32))
+        if ch.column.max_rep > 0:
+            nest = batch.nesting(c)
+            for k in range(nest.num_levels):
+                lv = nest.levels[k]
+                if lv.offsets:
+                    arrays.append((name + f"nest{k}_offsets", lv.offsets, lv.num_lists + 1, np.int32, np.float64))
+                if lv.validity:
+                    arrays.append((name + f"nest{k}_validity", lv.validity, lv.num_lists, np.uint8, np.float32))
+            if nest.leaf_validity:
+                arrays.append((name + "leaf_validity", nest.leaf_validity, nest.num_leaf_slots, np.uint8, np.float32))
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    total = 0
+    for name, ptr, n, src, dst in arrays:
+        n = int(n)
+        cap = share // np.dtype(dst).itemsize
+        if n <= cap:
+            got = ctx.d2h_array(ptr, n, src)
+        else:
+            blk = max(1, min(DUMP_BLOCK, cap))  # (thousands of arrays: smaller blocks keep the total in budget)
+            rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+            picks = np.sort(rng.choice(n // blk, size=max(1, cap // blk), replace=False))
+            got = np.concatenate([ctx.d2h_array(ptr + int(p) * blk * np.dtype(src).itemsize, blk, src) for p in picks])
+        out = got.astype(dst)
+        np.save(os.path.join(out_dir, name + ".npy"), out)
+        total += out.nbytes
+    return len(arrays), total
 
 
 def timed_block(ctx, native, f, rg0, rg1, steps, warmup, barrier_sync, pinned=True, verify=None):
@@ -853,6 +935,12 @@ def main():
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU (default: the config's)")
     ap.add_argument("--codec", default=None, choices=["snappy", "gzip"],
                     help="c5 / c5z: the page codec (default SNAPPY, as configs[4] names)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them decoded as DIR/<name>.npy (float32 / "
+                         "float64; a fixed seeded sample of the larger arrays: dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: profiled passes (kernels, roofline), CPU "
+                         "baseline and bit-exact check, end-to-end passes, next_row, c3_strong, c1_x10, mixed_1b")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (pinned H2D + decode) pass")
@@ -870,6 +958,8 @@ def main():
     # (LOCAL_RANK modulo their count) and reduce over gloo (RCCL refuses two ranks on one GPU)
     ap.add_argument("--share-gpu", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_cpu = args.no_e2e = args.no_c3 = args.no_mixed = args.no_next_row = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -982,21 +1072,30 @@ def main():
     if strong:
         pkg.shard.check_cover(blocks, f.num_row_groups, f.num_rows)
     batch.sync()
-    # profiled passes: every kernel between HIP events on the decode stream
-    ctx.set_profile(True)
-    batch.reset_stats()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        batch.run()
-    batch.sync()
-    prof_ms = (time.perf_counter() - t0) / args.steps * 1e3
-    check_statuses(batch, hb.num_chunks, native, "after the profiled steps")
-    stats = batch.kernel_stats()
-    ctx.set_profile(False)
+    if args.dump_outputs:  # (before any other run of the batch: the last timed step's outputs)
+        t0 = time.perf_counter()
+        nfiles, nbytes = dump_outputs(ctx, batch, hb.chunks(), ncols, rg0, args.dump_outputs,
+                                      prefix=f"rank{rank}_" if world > 1 else "")
+        log(f"rank {rank}: wrote {nfiles} arrays ({nbytes / 1e6:.1f} MB) of the last timed step to "
+            f"{args.dump_outputs} in {time.perf_counter() - t0:.2f}s")
     ms_per_step = elapsed / args.steps * 1e3
     value = total_written * args.steps / elapsed / 1e9
-
-    kernels, roof, all_ms = kernel_table(stats, desc, my_rows)
+    kernels, roof, all_ms, launch = None, None, None, None
+    if args.full:
+        # profiled passes: every kernel between HIP events on the decode stream
+        ctx.set_profile(True)
+        batch.reset_stats()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            batch.run()
+        batch.sync()
+        prof_ms = (time.perf_counter() - t0) / args.steps * 1e3
+        check_statuses(batch, hb.num_chunks, native, "after the profiled steps")
+        stats = batch.kernel_stats()
+        ctx.set_profile(False)
+        kernels, roof, all_ms = kernel_table(stats, desc, my_rows)
+        launch = ("direct launch of the one kernel (k_flat) per step" if "k_flat" in kernels else
+                  "hipGraph replay per step") + " (profiled direct launches: %.4f ms/step)" % prof_ms
     if roof and roof["algo_bytes_per_launch"] < MALL_BYTES:
         # the dominant kernel's whole working set fits the 256 MiB Infinity Cache and stays resident
         # from step to step (MI355X_MICROARCH.md): its rate is an upper bound, not HBM evidence
@@ -1164,7 +1263,7 @@ def main():
         hb = None
         c3 = c3_strong_record(args, ctx, native, pkg, datasets, world, rank, local, dist, barrier_sync, log)
     c1_x10 = None
-    if world == 1 and args.workload == "c1":
+    if args.full and world == 1 and args.workload == "c1":
         c1_x10 = c1_x10_record(args, ctx, native, datasets, barrier_sync)
     if not args.no_mixed and args.workload != "mixed":
         if hb is not None:
@@ -1184,8 +1283,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
-            "launch": ("direct launch of the one kernel (k_flat) per step" if "k_flat" in kernels else
-                       "hipGraph replay per step") + " (profiled direct launches: %.4f ms/step)" % prof_ms,
+            "full": args.full,
+            "launch": launch,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,

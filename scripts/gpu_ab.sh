@@ -12,7 +12,7 @@ if [ "${TESTS:-0}" = 1 ]; then
   rc=$?; echo "gpu_tests rc=$rc"; tail -3 "$OUT/gpu_tests.log"; [ $rc -eq 0 ] || exit $rc
 fi
 for w in ${WORKLOADS:-c4}; do
-  A="--workload $w --steps ${STEPS:-10} --warmup 2 --no-cpu --no-e2e --no-c3 --no-mixed --no-next-row ${AB_ARGS}"
+  A="--full --workload $w --steps ${STEPS:-10} --warmup 2 --no-cpu --no-e2e --no-c3 --no-mixed --no-next-row ${AB_ARGS}"
   for r in $(seq 1 ${ROUNDS:-1}); do
     for v in ${VARIANTS:-X=1}; do
       tag=${w}_${v//[=,\/]/_}_r$r

@@ -15,7 +15,7 @@ run() {  # run <name> <timeout> <bench args> -- <rocprof args...>
   echo "== $name rc=$rc"; tail -n 2 "$OUT/$name.log" | cut -c1-300
   if [ $rc -ne 0 ]; then exit $rc; fi
 }
-SKIP="--no-cpu --no-e2e --no-c3 --no-mixed --no-next-row"
+SKIP="--full --no-cpu --no-e2e --no-c3 --no-mixed --no-next-row"
 for w in ${WORKLOADS:-c2 c4 mixed}; do
   case $w in
     c2) A="--steps 10 --warmup 2 $SKIP" ;;

@@ -22,5 +22,5 @@ if [ -z "$SKIP_SMOKE" ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  step bench ${BENCH_TIMEOUT:-900} python bench.py ${BENCH_ARGS:---steps 20 --warmup 5}
+  step bench ${BENCH_TIMEOUT:-900} python bench.py ${BENCH_ARGS:---full --steps 20 --warmup 5}
 fi

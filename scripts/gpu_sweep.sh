@@ -14,7 +14,7 @@ step() {
   if grep -q "illegal memory access\|Memory access fault" "gpurun_out/sweep/$name.log"; then exit 3; fi
   return 0
 }
-A="--steps 10 --warmup 2 --no-c3 --no-mixed --no-next-row ${SWEEP_ARGS}"
+A="--full --steps 10 --warmup 2 --no-c3 --no-mixed --no-next-row ${SWEEP_ARGS}"
 for w in ${WORKLOADS:-c1 c3 c4 c5 c5z}; do
   step bench_$w 400 python bench.py --workload $w $A
 done

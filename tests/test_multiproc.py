@@ -128,7 +128,7 @@ def test_bench_self_launch_two_ranks():
     both plans (blocks that tile the file) and the reductions (sum of bytes, max of time) are checked
     here."""
     rows, c3rows, mrows = 20_000, 300_000, 256_000
-    d = _bench_dry(2, "--rows", str(rows), "--c3-rows", str(c3rows), "--mixed-rows", str(mrows))
+    d = _bench_dry(2, "--full", "--rows", str(rows), "--c3-rows", str(c3rows), "--mixed-rows", str(mrows))
     assert d["dry_run"] and d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["config"]["workload"].startswith("C2") and d["config"]["rows_total"] == 2 * rows
     sh = d["shards"]
@@ -155,13 +155,20 @@ def test_bench_single_gpu_scaling_proxy():
     """At N=1 the c3_strong sub-record carries the single-GPU proxy of the 1->8 curve: the whole C3
     file and rank 0's block of shard.row_group_block(128, N, 0) for N = 2, 4, 8."""
     c3rows = 200_000
-    d = _bench_dry(1, "--rows", "10000", "--c3-rows", str(c3rows))
+    d = _bench_dry(1, "--full", "--rows", "10000", "--c3-rows", str(c3rows))
     assert d["n_gpus"] == 1 and d["scaling"] == "weak"
     c3 = d["c3_strong"]
     assert c3["n_gpus"] == 1 and c3["decoded_bytes_total"] == 8 * c3rows
     assert [(p["n_gpus"], p["rank0_row_groups"]) for p in c3["proxy"]] == [(2, [0, 64]), (4, [0, 32]), (8, [0, 16])]
     for p in c3["proxy"]:
         assert abs(p["rank0_decoded_bytes"] * p["n_gpus"] - c3["decoded_bytes_total"]) <= 8 * p["n_gpus"] * 128
+
+
+def test_bench_plain_run_has_no_sub_records():
+    """Without --full the line is the main workload's alone: no c3_strong, no mixed_1b."""
+    d = _bench_dry(2, "--rows", "10000", "--c3-rows", "200000", "--mixed-rows", "256000")
+    assert d["scaling"] == "weak" and d["config"]["rows_total"] == 20000
+    assert d["c3_strong"] is None and d["mixed_1b"] is None
 
 
 def test_bench_strong_main_line():
