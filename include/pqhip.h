@@ -120,9 +120,10 @@ typedef enum pqh_status {
   PQH_ERR_INTERNAL = 34,              /* a device consistency guard fired (an index outside its buffer,
                                          a look-back that never completed): a bug, never a property of
                                          the input -- the chunk's outputs are undefined */
-  PQH_ERR_UNSUPPORTED_CODEC = 35      /* the chunk's codec is not decoded by this library (ZSTD, LZ4,
-                                         BROTLI, LZO, or any codec a caller registers with
-                                         RegisterBlockCompressor, compress.go:119-129,160,182-187): set by
+  PQH_ERR_UNSUPPORTED_CODEC = 35      /* the chunk's codec is not decoded by this library (ZSTD unless
+                                         loaded with PQH_LOAD_ZSTD, LZ4, BROTLI, LZO, or any codec a
+                                         caller registers with RegisterBlockCompressor,
+                                         compress.go:119-129,160,182-187): set by
                                          the page walker before any page of the chunk is read, never
                                          a property of the data -- the caller decodes the chunk with the
                                          reference's own readChunk / pageReader path */
@@ -184,7 +185,9 @@ typedef struct pqh_codec_page {
   int32_t src_len;      /* source bytes, raw prefix included */
   int32_t image_len;    /* == pqh_page.image_len: the header's uncompressed page size */
   int32_t raw_len;      /* leading bytes stored uncompressed (DataPageV2 levels, page_v2.go:116-125) */
-  int32_t codec;        /* PQH_CODEC_SNAPPY, or PQH_CODEC_UNCOMPRESSED for a plain copy */
+  int32_t codec;        /* PQH_CODEC_SNAPPY, PQH_CODEC_GZIP or PQH_CODEC_ZSTD (6: the values section is
+                           a sequence of RFC 8878 frames, decoded by k_zstd), or
+                           PQH_CODEC_UNCOMPRESSED for a plain copy */
   int32_t chunk;        /* owning chunk in the host batch */
   int32_t reserved;
 } pqh_codec_page;
@@ -423,7 +426,8 @@ int pqh_file_chunk_check(const pqh_file* f, int32_t rg, int32_t column, int32_t 
 
 /* The caller's codec registry (the reference's `compressors` map, compress.go:16-33,160-187; by
  * default UNCOMPRESSED, GZIP, SNAPPY and ZSTD, as its init registers them).  A chunk whose codec is
- * registered but not decoded by this library (any codec but UNCOMPRESSED / SNAPPY / GZIP) fails its
+ * registered but not decoded by this library (any codec but UNCOMPRESSED / SNAPPY / GZIP, and ZSTD
+ * unless loaded with PQH_LOAD_ZSTD) fails its
  * load with PQH_ERR_UNSUPPORTED_CODEC before any of its pages is read: the caller decodes that chunk
  * with the reference's own readChunk / pageReader path.  A codec in no registry fails
  * as the reference fails it (decompressBlock: "method not supported"): PQH_ERR_DECOMPRESS at the
@@ -489,6 +493,20 @@ int pqh_batch_create_staged(pqh_ctx* ctx, const pqh_host_batch* hb, pqh_batch** 
  * compressed and k_gzip (one workgroup per page: Go's multistream gzip.Reader rules for members,
  * headers and CRC-32 / ISIZE trailers; RFC 1951 inflate) rebuilds the images.  The flags combine. */
 #define PQH_LOAD_DEVICE_GZIP 2u
+/* ZSTD (zstdCompressor.DecompressBlock, compress.go:79-105: klauspost/compress/zstd DecodeAll), opt-in.
+ * With PQH_LOAD_ZSTD a chunk whose codec is ZSTD, in a file whose registry holds ZSTD
+ * (pqh_file_set_codecs), is walked and decompressed by this library as a GZIP chunk is: a page that
+ * fails to decode, or decodes to another size than its header's, ends the chunk there with
+ * PQH_ERR_DECOMPRESS, the pages before it listed.  Without the flag (or with ZSTD absent from the
+ * registry) nothing changes: PQH_ERR_UNSUPPORTED_CODEC (or "method not supported").  The decoder is
+ * this library's own (RFC 8878; no libzstd, no dictionaries) and follows the reference's decoder where
+ * libzstd differs: blocks and literals over the window size, windows over 512 MiB,
+ * match offsets over the window size and Huffman streams not exactly consumed are errors.
+ * PQH_LOAD_DEVICE_ZSTD implies PQH_LOAD_ZSTD and keeps the pages of ZSTD chunks compressed in the
+ * source payload (codec pages with codec 6): k_zstd, one workgroup per page, rebuilds their images,
+ * under the same routing (PQH_DEVICE_CODEC_MAX_RATIO) and failure rules as the other device codecs. */
+#define PQH_LOAD_ZSTD 4u
+#define PQH_LOAD_DEVICE_ZSTD 8u
 int pqh_file_load_ex(pqh_file* f, int32_t rg_begin, int32_t rg_end, const int32_t* columns, int32_t num_columns,
                      int32_t validate_crc, uint32_t flags, pqh_host_batch** out);
 

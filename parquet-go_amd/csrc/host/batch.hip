@@ -110,8 +110,8 @@ const char* kKernelNames[] = {"k_prologue", "k_scan", "k_expand", "k_dict_global
                               "k_delta_fused", "k_ba_wstitch", "k_ba_wemit",   "k_snappy",
                               "k_ba_wcopy",   "k_gzip",      "k_snap_spec",  "k_snap_stitch",
                               "k_snap_emit",  "k_snap_fixup", "k_ba_chain",   "k_flat",
-                              "k_expand_lev", "k_delta_split"};
-constexpr int kNumKernels = 33;
+                              "k_expand_lev", "k_delta_split", "k_zstd"};
+constexpr int kNumKernels = 34;
 // Batches with at least this many delta streams decode each stream in one workgroup (k_delta_page);
 // fewer streams go through per-tile sums, a page scan and per-tile expands (more parallelism).
 constexpr size_t kDeltaPageModeMin = 256;
@@ -383,6 +383,9 @@ struct pqh_batch {
   pqh_codec_page* d_codec = nullptr;
   int32_t codec_n = 0;
   int32_t codec_gzip = 0;  // GZIP pages among them (k_gzip)
+  int32_t codec_zstd = 0;  // ZSTD pages among them (k_zstd)
+  int64_t* d_zstd_off = nullptr;  // per codec page: its literals scratch in d_zstd_lits (zstd_plan)
+  uint8_t* d_zstd_lits = nullptr;
   int32_t* d_codec_status = nullptr;
   std::vector<int32_t> codec_status;  // host copy after sync (per page)
   SnapPlan snap;                      // multi-workgroup SNAPPY tables and scratch (snappy_mw.h)
@@ -1452,6 +1455,11 @@ hipError_t enqueue_run(pqh_batch* b, hipStream_t s, bool prof) {
       return launch_gzip(b->d_codec, b->codec_n, static_cast<const uint8_t*>(b->d_src),
                          static_cast<uint8_t*>(b->owned_payload), b->d_codec_status, st);
     });
+  if (e == hipSuccess && b->codec_zstd)
+    e = timed(33, b->codec_zstd, s, [&](hipStream_t st) {
+      return launch_zstd(b->d_codec, b->codec_n, static_cast<const uint8_t*>(b->d_src),
+                         static_cast<uint8_t*>(b->owned_payload), b->d_codec_status, b->d_zstd_off, b->d_zstd_lits, st);
+    });
   // repeated columns carry long level streams: a workgroup per page splits their notNull count
   const bool wide = std::any_of(b->hchunks.begin(), b->hchunks.end(), [](const DevChunk& c) { return c.max_rep > 0; });
   if (e == hipSuccess && b->ba_fuse_on) {  // fused chains: tickets, fallback flag (k_scan's too), look-back words
@@ -2364,6 +2372,19 @@ int create_codec_batch(pqh_ctx* ctx, const pqh_host_batch* hb, void* d_src, pqh_
     *out = nullptr;
     return rc;
   }
+  b->codec_zstd = int32_t(std::count_if(hb->codec_pages.begin(), hb->codec_pages.end(),
+                                        [](const pqh_codec_page& c) { return c.codec == PQH_CODEC_ZSTD; }));
+  if (e == hipSuccess && b->codec_zstd) {  // k_zstd's literals scratch: with the batch (a streaming context: its arena)
+    int64_t zbytes = 0;
+    const std::vector<int64_t> zoff = zstd_plan(hb->codec_pages.data(), b->codec_n, &zbytes);
+    if ((rc = dalloc(b, reinterpret_cast<void**>(&b->d_zstd_off), sizeof(int64_t) * zoff.size())) ||
+        (rc = dalloc(b, reinterpret_cast<void**>(&b->d_zstd_lits), size_t(zbytes)))) {
+      pqh_batch_destroy(b);
+      *out = nullptr;
+      return rc;
+    }
+    e = bounce_h2d(ctx, b->d_zstd_off, zoff.data(), sizeof(int64_t) * zoff.size());
+  }
   if (e != hipSuccess) {
     pqh_batch_destroy(b);
     *out = nullptr;
@@ -2505,11 +2526,24 @@ int pqh_decompress_pages(pqh_ctx* ctx, const pqh_codec_page* pages, int32_t num_
   }
   if (e == hipSuccess && std::any_of(pages, pages + num_pages, [](const pqh_codec_page& c) { return c.codec == PQH_CODEC_GZIP; }))
     e = launch_gzip(dp, num_pages, static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst), ds, ctx->stream);
+  int64_t* zo = nullptr;
+  uint8_t* zl = nullptr;
+  if (e == hipSuccess && std::any_of(pages, pages + num_pages, [](const pqh_codec_page& c) { return c.codec == PQH_CODEC_ZSTD; })) {
+    int64_t zbytes = 0;
+    const std::vector<int64_t> zoff = zstd_plan(pages, num_pages, &zbytes);
+    e = hipMalloc(&zo, sizeof(int64_t) * zoff.size());
+    if (e == hipSuccess) e = hipMalloc(&zl, size_t(zbytes));
+    if (e == hipSuccess) e = bounce_h2d(ctx, zo, zoff.data(), sizeof(int64_t) * zoff.size());
+    if (e == hipSuccess)
+      e = launch_zstd(dp, num_pages, static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst), ds, zo, zl, ctx->stream);
+  }
   if (e == hipSuccess) e = bounce_d2h(ctx, status, ds, sizeof(int32_t) * size_t(num_pages));
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (dp) hipFree(dp);
   if (ds) hipFree(ds);
   if (scratch) hipFree(scratch);
+  if (zo) hipFree(zo);
+  if (zl) hipFree(zl);
   if (e != hipSuccess) return set_err(ctx, PQH_ERR_HIP, std::string("pqh_decompress_pages: ") + hipGetErrorString(e));
   return PQH_OK;
 }

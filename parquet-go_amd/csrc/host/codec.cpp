@@ -1,10 +1,13 @@
 // codec.cpp — see codec.h.
 #include "codec.h"
 
+#include "../kernels/zstd_core.h"
+
 #include <zlib.h>
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 namespace pqhip {
 
@@ -336,6 +339,152 @@ static bool gzip_into(const uint8_t* src, size_t n, uint8_t* dst, size_t expecte
   return ok && pos == expected;
 }
 
+// ZSTD (RFC 8878) without libzstd: the shared core (kernels/zstd_core.h) plus this serial executor.
+// Concatenated and skippable frames as the reference's DecodeAll loops over them
+// (klauspost/compress/zstd decoder.go:331-399).  0: valid, 1: corrupt, 2: more than `cap` bytes.
+namespace {
+
+struct ZstdBlockScratch {
+  zs::Tables t;
+  zs::HufScratch hs;
+  zs::SeqScratch ss;
+  uint8_t weights[256];
+  uint8_t lits[zs::kBlockMax];
+};
+
+int zstd_block(const uint8_t* p, size_t size, uint64_t window, ZstdBlockScratch& z, uint8_t* dst, size_t cap,
+               size_t frame_start, size_t& out) {
+  zs::Literals l;
+  if (!zs::literals_header(p, int64_t(size), window, &l)) return 1;
+  const uint8_t* lit = z.lits;
+  const uint8_t* q = p + l.header;
+  if (l.type == 0) {
+    lit = q;
+  } else if (l.type == 1) {
+    memset(z.lits, q[0], l.regen);
+  } else {
+    uint32_t rem = l.comp;
+    if (l.type == 2) {
+      int count;
+      const int used = zs::huf_read_weights(q, rem, z.weights, &count, &z.hs);
+      if (used < 0) return 1;
+      z.t.huf_log = -1;
+      if (!zs::huf_build(z.weights, count, z.t.huf, &z.t.huf_log)) return 1;
+      q += used;
+      rem -= uint32_t(used);
+    } else if (z.t.huf_log < 0) {
+      return 1;  // treeless with no table yet
+    }
+    zs::Streams s;
+    if (!zs::split_streams(q, rem, l.regen, l.streams, &s)) return 1;
+    for (uint32_t k = 0; k < l.streams; k++)
+      if (!zs::huf_stream(q + s.src[k], s.len[k], z.t.huf, z.t.huf_log, z.lits + s.dst[k], s.out[k])) return 1;
+  }
+  const uint8_t* sp = p + l.header + l.comp;
+  const int64_t sn = int64_t(size) - l.header - l.comp;
+  uint32_t nseq;
+  const int at = zs::seq_header(sp, sn, &z.t, &nseq, &z.ss);
+  if (at < 0) return 1;
+  const size_t block_max = size_t(std::min<uint64_t>(window, zs::kBlockMax));
+  const size_t block_start = out;
+  uint32_t lpos = 0;
+  if (nseq) {
+    zs::SeqWalk w;
+    if (!zs::seq_begin(&w, &z.t, sp + at, sn - at, nseq)) return 1;
+    for (uint32_t i = 0; i < nseq; i++) {
+      uint32_t ll, ml, off;
+      if (!zs::seq_next(&w, &z.t, &ll, &ml, &off)) return 1;
+      if (ll > l.regen - lpos) return 1;  // more literals than the block has
+      if (out - block_start + ll + ml > block_max) return 1;
+      if (cap - out < size_t(ll) + ml) return 2;
+      memcpy(dst + out, lit + lpos, ll);
+      lpos += ll;
+      out += ll;
+      if (off > out - frame_start || off > window) return 1;  // before the frame's output / the window
+      if (off >= ml) {
+        memcpy(dst + out, dst + out - off, ml);
+      } else {
+        for (uint32_t k = 0; k < ml; k++) dst[out + k] = dst[out + k - off];  // overlapping: forward copy
+      }
+      out += ml;
+    }
+    if (w.bits.left != 0) return 1;  // the bitstream is not exactly consumed
+  }
+  const uint32_t tail = l.regen - lpos;
+  if (out - block_start + tail > block_max) return 1;
+  if (cap - out < tail) return 2;
+  memcpy(dst + out, lit + lpos, tail);
+  out += tail;
+  return 0;
+}
+
+int zstd_run(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* produced) {
+  std::unique_ptr<ZstdBlockScratch> z(new ZstdBlockScratch);
+  size_t in = 0, out = 0;
+  while (in < n) {
+    zs::Frame f;
+    if (!zs::frame_header(src + in, n - in, &f)) return 1;
+    in += f.header_size;
+    if (f.skippable) continue;
+    zs::tables_reset(&z->t);
+    const size_t frame_start = out;
+    for (;;) {
+      zs::Block b;
+      if (n - in < 3 || !zs::block_header(src + in, f.window, &b)) return 1;
+      in += 3;
+      if (b.type == 0) {
+        if (n - in < b.size) return 1;
+        if (cap - out < b.size) return 2;
+        memcpy(dst + out, src + in, b.size);
+        in += b.size;
+        out += b.size;
+      } else if (b.type == 1) {
+        if (n - in < 1) return 1;
+        if (cap - out < b.size) return 2;
+        memset(dst + out, src[in], b.size);
+        in += 1;
+        out += b.size;
+      } else {
+        if (n - in < b.size) return 1;
+        const int rc = zstd_block(src + in, b.size, f.window, *z, dst, cap, frame_start, out);
+        if (rc) return rc;
+        in += b.size;
+      }
+      if (b.last) break;
+    }
+    if (f.has_size && out - frame_start != f.content_size) return 1;
+    if (f.checksum) {
+      if (n - in < 4 || zs::le32(src + in) != uint32_t(zs::xxh64(dst + frame_start, out - frame_start))) return 1;
+      in += 4;
+    }
+  }
+  *produced = out;
+  return 0;
+}
+
+}  // namespace
+
+bool zstd_decompress(const uint8_t* src, size_t n, size_t expected, std::vector<uint8_t>& dst) {
+  dst.clear();
+  dst.resize(expected > 0 ? expected : 64);
+  for (;;) {
+    size_t got = 0;
+    const int rc = zstd_run(src, n, dst.data(), dst.size(), &got);
+    if (rc == 0) {
+      dst.resize(got);
+      return true;
+    }
+    if (rc == 1 || dst.size() >= (size_t(1) << 32)) return false;
+    dst.resize(dst.size() * 2);
+  }
+}
+
+// ZSTD frames straight into dst[expected]: fails on corrupt input or any other output size.
+static bool zstd_into(const uint8_t* src, size_t n, uint8_t* dst, size_t expected) {
+  size_t got = 0;
+  return zstd_run(src, n, dst, expected, &got) == 0 && got == expected;
+}
+
 bool decompress_into(int codec, const uint8_t* src, size_t n, uint8_t* dst, size_t expected) {
   switch (codec) {
     case 0:
@@ -346,6 +495,8 @@ bool decompress_into(int codec, const uint8_t* src, size_t n, uint8_t* dst, size
       return snappy_into(src, n, dst, expected);
     case 2:
       return gzip_into(src, n, dst, expected);
+    case 6:
+      return zstd_into(src, n, dst, expected);
     default:
       return false;
   }
@@ -360,6 +511,8 @@ bool decompress_block(int codec, const uint8_t* src, size_t n, size_t expected, 
       return snappy_decompress(src, n, dst);
     case 2:
       return gzip_decompress(src, n, expected, dst);
+    case 6:
+      return zstd_decompress(src, n, expected, dst);
     default:
       return false;
   }

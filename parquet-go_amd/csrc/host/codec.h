@@ -3,6 +3,8 @@
 //   SNAPPY:       block format of github.com/golang/snappy v0.0.4 (snappy.Decode / snappy.Encode,
 //                 compress.go:43-49) — hand-written, no snappy library in this image
 //   GZIP:         RFC 1952 via zlib (Go compress/gzip, compress.go:51-77)
+//   ZSTD:         RFC 8878 frames (klauspost/compress/zstd DecodeAll, compress.go:79-105) --
+//                 hand-written over kernels/zstd_core.h, no libzstd; decode only
 #pragma once
 
 #include <cstddef>
@@ -22,6 +24,7 @@ bool decompress_into(int codec, const uint8_t* src, size_t n, uint8_t* dst, size
 bool snappy_decompress(const uint8_t* src, size_t n, std::vector<uint8_t>& dst);
 void snappy_compress(const uint8_t* src, size_t n, std::vector<uint8_t>& dst);
 bool gzip_decompress(const uint8_t* src, size_t n, size_t expected, std::vector<uint8_t>& dst);
+bool zstd_decompress(const uint8_t* src, size_t n, size_t expected, std::vector<uint8_t>& dst);
 bool gzip_compress(const uint8_t* src, size_t n, std::vector<uint8_t>& dst);
 bool compress_block(int codec, const uint8_t* src, size_t n, std::vector<uint8_t>& dst);
 

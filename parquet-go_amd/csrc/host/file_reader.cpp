@@ -346,6 +346,13 @@ double device_codec_max_ratio() {
   return v ? atof(v) : 0.95;
 }
 
+// ZSTD chunks go to the device when the flag asks for it and the file's registry holds ZSTD (a
+// ZSTD chunk of a file whose registry lacks it fails as before, on the host route)
+bool device_zstd(const pqh_file* f, uint32_t flags) {
+  return (flags & PQH_LOAD_DEVICE_ZSTD) &&
+         std::find(f->codecs.begin(), f->codecs.end(), int32_t(PQH_CODEC_ZSTD)) != f->codecs.end();
+}
+
 // Plan: readChunk + readPages for one chunk (chunk_reader.go:182-362), page by page in the
 // reference's order of checks.  The walk stops at the first page it cannot read (host_status, with
 // the pages before it listed); the checks of each listed page that belong to the decoders (the
@@ -368,9 +375,13 @@ void plan_chunk(const pqh_file* f, const ColumnMeta& col, const ChunkMeta& m, in
   // property of the data: the chunk is handed back before any page is read, never reported as a
   // corrupt page.  (A codec in no registry fails as the reference fails it: decompressBlock's
   // "method not supported", at the first page's block -- materialise / decompress_into.)
-  if (m.codec != PQH_CODEC_UNCOMPRESSED && m.codec != PQH_CODEC_SNAPPY && m.codec != PQH_CODEC_GZIP &&
-      std::find(f->codecs.begin(), f->codecs.end(), m.codec) != f->codecs.end())
+  // (ZSTD is decoded here only when the caller asks for it: PQH_LOAD_ZSTD / PQH_LOAD_DEVICE_ZSTD.)
+  const bool registered = std::find(f->codecs.begin(), f->codecs.end(), m.codec) != f->codecs.end();
+  const bool zstd = m.codec == PQH_CODEC_ZSTD && registered && (flags & (PQH_LOAD_ZSTD | PQH_LOAD_DEVICE_ZSTD));
+  if (m.codec != PQH_CODEC_UNCOMPRESSED && m.codec != PQH_CODEC_SNAPPY && m.codec != PQH_CODEC_GZIP && !zstd &&
+      registered)
     return fail(PQH_ERR_UNSUPPORTED_CODEC);
+  if (m.codec == PQH_CODEC_ZSTD && !zstd) w.codec = -1;  // in no registry: "method not supported", whatever the flags
   int64_t pos = m.has_dict_offset ? m.dict_page_offset : m.data_page_offset;
   if (pos < 0) return fail(PQH_ERR_IO);  // Seek: negative position
   int64_t count = 0;
@@ -379,7 +390,8 @@ void plan_chunk(const pqh_file* f, const ColumnMeta& col, const ChunkMeta& m, in
   // this chunk's pages stay compressed for the device (the layout is the device-codec one whenever
   // some selected chunk's codec is decoded on the device)
   const bool dev = dev_codecs && ((m.codec == PQH_CODEC_SNAPPY && (flags & PQH_LOAD_DEVICE_SNAPPY)) ||
-                                  (m.codec == PQH_CODEC_GZIP && (flags & PQH_LOAD_DEVICE_GZIP)));
+                                  (m.codec == PQH_CODEC_GZIP && (flags & PQH_LOAD_DEVICE_GZIP)) ||
+                                  (m.codec == PQH_CODEC_ZSTD && device_zstd(f, flags)));
   const double max_ratio = device_codec_max_ratio();
   while (m.total_compressed - count > 0) {
     // readThrift(PageHeader): reads past the end of the file fail like any short read
@@ -619,14 +631,15 @@ int file_load(pqh_ctx* ctx, pqh_file* f, int32_t rg_begin, int32_t rg_end, const
   // device codecs only when some selected chunk has a codec the flags put on the device
   // (otherwise the plain layout)
   bool dev = false;
-  if (flags & (PQH_LOAD_DEVICE_SNAPPY | PQH_LOAD_DEVICE_GZIP))
+  if (flags & (PQH_LOAD_DEVICE_SNAPPY | PQH_LOAD_DEVICE_GZIP | PQH_LOAD_DEVICE_ZSTD))
     for (int32_t rg = rg_begin; rg < rg_end && !dev; rg++)
       for (int32_t i = 0; i < num_columns && !dev; i++) {
         const RowGroupMeta& g = f->rgs[size_t(rg)];
         if (size_t(columns[i]) >= g.chunks.size() || !g.chunks[size_t(columns[i])].has_meta) continue;
         const int32_t c = g.chunks[size_t(columns[i])].codec;
         dev = (c == PQH_CODEC_SNAPPY && (flags & PQH_LOAD_DEVICE_SNAPPY)) ||
-              (c == PQH_CODEC_GZIP && (flags & PQH_LOAD_DEVICE_GZIP));
+              (c == PQH_CODEC_GZIP && (flags & PQH_LOAD_DEVICE_GZIP)) ||
+              (c == PQH_CODEC_ZSTD && device_zstd(f, flags));
       }
   // walker threads: one per hardware thread up to 16 (the host share a GPU box grants), or
   // PQH_WALK_THREADS (a streaming ring leaves cores to the batch creation beside its walks)

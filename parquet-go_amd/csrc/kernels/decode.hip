@@ -15,6 +15,7 @@
 
 #include "launch.h"
 #include "pqhip.h"
+#include "zstd_core.h"  // (outside the namespace: pqhip::zs, shared with host/codec.cpp)
 
 namespace pqhip {
 
@@ -1259,6 +1260,7 @@ __device__ __forceinline__ void tile_bool_plain(const DevBatch& b, const Tile& t
 #include "snappy_mw.h"
 #include "snappy_emit.h"
 #include "gzip_impl.h"
+#include "zstd_impl.h"
 
 __global__ __launch_bounds__(256) void k_expand(DevBatch b, const Tile* tiles) {
   __shared__ TileLds L;
@@ -1607,7 +1609,7 @@ std::vector<int32_t> snap_plan_tables(const pqh_codec_page* pages, int32_t n, in
         nw = (body + kSnWin - 1) / kSnWin;
         if (raw <= c.image_len) nu = (out + kSnUnit - 1) / kSnUnit;
       }
-    } else if (c.codec != PQH_CODEC_GZIP) {
+    } else if (c.codec != PQH_CODEC_GZIP && c.codec != PQH_CODEC_ZSTD) {  // (their own kernels': no windows, no units)
       nu = ((c.src_len < c.image_len ? c.src_len : c.image_len) + int64_t(kSnUnit) - 1) / kSnUnit;
     }
     for (int64_t j = 0; j < nw; j++) wp.push_back(i);
@@ -1666,6 +1668,24 @@ hipError_t launch_gzip(const pqh_codec_page* pages, int32_t n, const uint8_t* sr
                        hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_gzip, dim3(n), dim3(256), 0, s, pages, src, dst, status);
+  return hipGetLastError();
+}
+
+std::vector<int64_t> zstd_plan(const pqh_codec_page* pages, int32_t n, int64_t* bytes) {
+  std::vector<int64_t> off(size_t(n), 0);
+  int64_t at = 0;
+  for (int32_t i = 0; i < n; i++) {
+    off[size_t(i)] = at;
+    if (pages[i].codec == PQH_CODEC_ZSTD) at += zstd_scratch_bytes(pages[i]);
+  }
+  *bytes = at + 64;
+  return off;
+}
+
+hipError_t launch_zstd(const pqh_codec_page* pages, int32_t n, const uint8_t* src, uint8_t* dst, int32_t* status,
+                       const int64_t* lits_off, uint8_t* lits, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_zstd, dim3(n), dim3(256), 0, s, pages, src, dst, status, lits_off, lits);
   return hipGetLastError();
 }
 

@@ -72,6 +72,12 @@ hipError_t launch_snappy_mw(const pqh_codec_page* pages, const SnapPlan& P, cons
 // GZIP pages of the same table (one workgroup per page; the other pages' workgroups exit at once).
 hipError_t launch_gzip(const pqh_codec_page* pages, int32_t n, const uint8_t* src, uint8_t* dst, int32_t* status,
                        hipStream_t s);
+// ZSTD pages of the same table (k_zstd, one workgroup per page).  zstd_plan: where each page's
+// literals scratch starts (lits_off, one entry per page) and the scratch's size in bytes; a page's
+// share is its decompressed values, at most 128 KiB (one block's literals).
+std::vector<int64_t> zstd_plan(const pqh_codec_page* pages, int32_t n, int64_t* bytes);
+hipError_t launch_zstd(const pqh_codec_page* pages, int32_t n, const uint8_t* src, uint8_t* dst, int32_t* status,
+                       const int64_t* lits_off, uint8_t* lits, hipStream_t s);
 hipError_t launch_scan(const DevBatch& b, hipStream_t s);
 // Fused PLAIN byte-array chains (bytearray_impl.h k_ba_chain): one workgroup per window of wins
 // (page-major), dispatched in `order`.

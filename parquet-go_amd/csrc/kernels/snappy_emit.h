@@ -509,6 +509,7 @@ __global__ __launch_bounds__(kSnT) void k_snap_emit(const pqh_codec_page* cps, c
   const int32_t k = u - page_unit0[p];
   const pqh_codec_page cp = cps[p];
   uint8_t* dst = dst_all + cp.image_offset;
+  if (cp.codec == PQH_CODEC_GZIP || cp.codec == PQH_CODEC_ZSTD) return;  // (no units: k_gzip's / k_zstd's)
   if (cp.codec != PQH_CODEC_SNAPPY) {  // a plain copy, unit by unit
     const int64_t len = cp.src_len < cp.image_len ? cp.src_len : cp.image_len;
     const int64_t U0 = int64_t(k) * kSnUnit;

@@ -431,13 +431,13 @@ __device__ int snappy_block(const uint8_t* src, int64_t n, uint8_t* dst, int64_t
 }
 
 // One workgroup per page: its image rebuilt at image_offset from its source bytes (codec 0: copied;
-// GZIP pages: k_gzip).
+// GZIP pages: k_gzip; ZSTD pages: k_zstd).
 __global__ __launch_bounds__(256) void k_snappy(const pqh_codec_page* cps, const uint8_t* src_all, uint8_t* dst_all,
                                                 int32_t* status, const int32_t* only) {
   __shared__ SnapLds E;
   if (only && !only[blockIdx.x]) return;  // (the multi-workgroup pipeline's page)
   const pqh_codec_page cp = cps[blockIdx.x];
-  if (cp.codec == PQH_CODEC_GZIP) return;  // k_gzip's
+  if (cp.codec == PQH_CODEC_GZIP || cp.codec == PQH_CODEC_ZSTD) return;  // k_gzip's / k_zstd's
   const uint8_t* src = src_all + cp.src_offset;
   uint8_t* dst = dst_all + cp.image_offset;
   int rc = PQH_OK;

@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void k_snap_stitch(const pqh_codec_page* cps, 
   const int tid = threadIdx.x, lane = tid & 63;
   const int32_t p = blockIdx.x;
   const pqh_codec_page cp = cps[p];
-  if (cp.codec == PQH_CODEC_GZIP || page_mode[p]) return;  // k_gzip's / k_snappy's
+  if (cp.codec == PQH_CODEC_GZIP || cp.codec == PQH_CODEC_ZSTD || page_mode[p]) return;  // k_gzip's / k_zstd's / k_snappy's
   if (cp.codec != PQH_CODEC_SNAPPY) {       // a plain copy (k_snap_emit's units)
     if (tid == 0) status[p] = cp.src_len == cp.image_len ? PQH_OK : PQH_ERR_DECOMPRESS;
     return;

@@ -79,6 +79,8 @@ class CodecPage(ctypes.Structure):
 
 LOAD_DEVICE_SNAPPY = 1
 LOAD_DEVICE_GZIP = 2
+LOAD_ZSTD = 4
+LOAD_DEVICE_ZSTD = 8
 
 
 class SchemaElement(ctypes.Structure):
@@ -446,15 +448,18 @@ class File:
         return self.L.pqh_file_chunk_check(self.h, rg, column, int(selected))
 
     def load(self, rg_begin, rg_end, columns, validate_crc=False, device_snappy=False, ctx=None,
-             device_gzip=False):
+             device_gzip=False, zstd=False, device_zstd=False):
         """Walk the pages of `columns` in row groups [rg_begin, rg_end).  device_snappy /
         device_gzip: SNAPPY / GZIP pages stay compressed (the batch decompresses them on the
-        device, k_snappy / k_gzip).  ctx: the
+        device, k_snappy / k_gzip).  zstd: ZSTD chunks are decompressed by this library instead of
+        failing with UNSUPPORTED_CODEC; device_zstd (implies zstd): their pages stay compressed for
+        k_zstd.  ctx: the
         payload is written into pinned memory from the context's pool (pqh_file_load_pinned), which
         Batch.staged adopts without a copy."""
         cols = (i32 * len(columns))(*columns)
         h = vp()
         flags = (LOAD_DEVICE_SNAPPY if device_snappy else 0) | (LOAD_DEVICE_GZIP if device_gzip else 0)
+        flags |= (LOAD_ZSTD if zstd else 0) | (LOAD_DEVICE_ZSTD if device_zstd else 0)
         if ctx is not None:
             rc = self.L.pqh_file_load_pinned(ctx.h, self.h, rg_begin, rg_end, cols, len(columns), int(validate_crc),
                                              flags, ctypes.byref(h))

@@ -158,15 +158,18 @@ def batch_columns(ctx, file, batch, hb, columns):
 
 
 def decode_chunks(ctx, file, rg_begin, rg_end, columns, validate_crc=False, return_batch=False, staged_runs=0,
-                  device_snappy=False, device_gzip=False):
+                  device_snappy=False, device_gzip=False, zstd=False, device_zstd=False):
     """Walk (host) and decode (GPU) the chunks of `columns` in row groups [rg_begin, rg_end).
 
     staged_runs > 0: end-to-end mode -- the page images stay in pinned host memory and each of the
     `staged_runs` runs copies them to HBM on the copy stream ahead of the decode.
     device_snappy / device_gzip: SNAPPY / GZIP pages are decompressed on the device (k_snappy /
     k_gzip) instead of the host.
+    zstd: ZSTD chunks are decompressed by this library (on the host) instead of failing with
+    UNSUPPORTED_CODEC; device_zstd (implies zstd): on the device (k_zstd).
     Returns a list of ColumnData in (row group, column) order."""
-    hb = file.load(rg_begin, rg_end, columns, validate_crc, device_snappy=device_snappy, device_gzip=device_gzip)
+    hb = file.load(rg_begin, rg_end, columns, validate_crc, device_snappy=device_snappy, device_gzip=device_gzip,
+                   zstd=zstd, device_zstd=device_zstd)
     if staged_runs:
         batch = native.Batch.staged(ctx, hb)
         for _ in range(staged_runs):
@@ -208,13 +211,15 @@ class RowGroupStream:
     batches of `slots` ranges.  Iterating yields (rg_begin, rg_end, native.Batch, host batch)."""
 
     def __init__(self, file, columns, rg_begin=0, rg_end=None, per_range=4, slots=3, device=0, validate_crc=False,
-                 threaded=True, device_snappy=False, device_gzip=False):
+                 threaded=True, device_snappy=False, device_gzip=False, zstd=False, device_zstd=False):
         self.file = file
         self.columns = list(columns)
         rg_end = file.num_row_groups if rg_end is None else rg_end
         self.ranges = [(a, min(a + per_range, rg_end)) for a in range(rg_begin, rg_end, per_range)]
         self.validate_crc = validate_crc
         self.load_kw = {"device_snappy": device_snappy, "device_gzip": device_gzip}
+        if zstd or device_zstd:  # (opt-in: passed on only when asked for)
+            self.load_kw.update(zstd=zstd, device_zstd=device_zstd)
         self.threaded = threaded
         self.ctxs = [native.Context(device, streaming=True) for _ in range(max(1, slots))]
         self.walk_s = 0.0
@@ -393,8 +398,10 @@ class FileReader:
     reference: rowGroupPosition is 1-based once a group is loaded, advanceIfNeeded loads the next
     group when the current one is exhausted or skipped, io.EOF past the last group (EOFError)."""
 
-    def __init__(self, source, *columns, device=0, validate_crc=False, ctx=None, columnar=True):
+    def __init__(self, source, *columns, device=0, validate_crc=False, ctx=None, columnar=True, zstd=False,
+                 device_zstd=False):
         self.file = native.File(source)
+        self.load_kw = {"zstd": zstd, "device_zstd": device_zstd}  # ZSTD chunks: decoded here when asked
         self.ctx = ctx or native.Context(device)
         self.validate_crc = validate_crc
         allc = self.file.columns()
@@ -440,7 +447,7 @@ class FileReader:
         self._loaded = None
         self._rows = None
         self._pending = None  # a NextBatch error belongs to the row group it came from
-        loaded = decode_chunks(self.ctx, self.file, rg, rg + 1, self.selected, self.validate_crc)
+        loaded = decode_chunks(self.ctx, self.file, rg, rg + 1, self.selected, self.validate_crc, **self.load_kw)
         # readRowGroupData (chunk_reader.go:375-404): column by column in schema order, the column
         # checks (skipChunk for the unselected ones), then readChunk; the first failure fails the group
         by_col = dict(zip(self.selected, loaded))
