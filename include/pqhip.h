@@ -211,7 +211,18 @@ typedef struct pqh_chunk_out {
   int32_t error_page;    /* page index (batch-global) of that error, or -1 */
   int32_t error_phase;   /* enum pqh_phase of that error */
   int64_t error_index;   /* value / level index of that error inside its page */
-  void* values;          /* dense not-null values, natural width, little endian (device) */
+  /* Dense not-null values, natural width, little endian (device).  Read-only for the caller, valid as
+   * long as the batch: it may point into the batch's payload instead of a buffer of its own.  That is
+   * the case for a chunk whose page images already are its values array -- a required, non-repeated
+   * INT32 / INT64 / FLOAT / DOUBLE / FIXED_LEN_BYTE_ARRAY(L > 0) column without a dictionary page,
+   * every page a PLAIN DATA_PAGE / DATA_PAGE_V2 of exactly num_values * value_size bytes (no level
+   * bytes), host_status PQH_OK, the images back to back (image_offset[i + 1] == image_offset[i] +
+   * image_len[i]) from a 64-byte aligned device address, in a batch without device-codec pages.
+   * pqh_file_load lays such chunks out that way; hand-built tables that miss a condition get a buffer
+   * of the batch's as before.  No kernel copies such a chunk (pqh_batch_paths.plain_alias_chunks
+   * counts them) and nothing ever writes through the pointer.  PQH_PLAIN_ALIAS=0 in the environment
+   * (read when a batch is created; for tests and A/B profiling) turns this off. */
+  void* values;
   int64_t* offsets;      /* BYTE_ARRAY: num_non_null + 1 byte offsets into bytes (device), else NULL */
   uint8_t* bytes;        /* BYTE_ARRAY data (device), else NULL */
   int64_t num_bytes;     /* BYTE_ARRAY data size */
@@ -358,7 +369,8 @@ typedef struct pqh_batch_paths {
   int32_t ba_fuse_fallbacks; /* k_ba_chain verifications that failed (then the scratch path) */
   int32_t regrows;           /* re-decodes after growing short byte-array outputs */
   int32_t graph_replay;      /* unprofiled runs replay a captured hipGraph */
-  int32_t reserved[2];
+  int32_t plain_alias_chunks; /* chunks whose values are handed out in place in the payload (pqh_chunk_out.values) */
+  int32_t reserved;
 } pqh_batch_paths;
 int pqh_batch_path_info(const pqh_batch* batch, pqh_batch_paths* out);
 int pqh_batch_chunk_out(const pqh_batch* batch, int32_t chunk, pqh_chunk_out* out);
@@ -453,7 +465,10 @@ int pqh_file_schema_element(const pqh_file* f, int32_t index, pqh_schema_element
                             int32_t name_capacity);
 
 /* Walk and decompress the pages of the given leaf columns for row groups [rg_begin, rg_end),
- * producing a page table and one payload of page images (8-byte aligned images). */
+ * producing a page table and one payload of page images.  Every image starts 64-byte aligned, except
+ * in a chunk whose PLAIN pages are its decoded values (see pqh_chunk_out.values): there only the
+ * first page is aligned and each next image starts where the one before it ends.  (Device-codec
+ * loads, pqh_file_load_ex with a PQH_LOAD_DEVICE_* flag that applies, keep every image aligned.) */
 int pqh_file_load(pqh_file* f, int32_t rg_begin, int32_t rg_end, const int32_t* columns,
                   int32_t num_columns, int32_t validate_crc, pqh_host_batch** out);
 int32_t pqh_host_batch_num_chunks(const pqh_host_batch* hb);

@@ -129,6 +129,9 @@ thread_local const char* g_fail_kernel = nullptr;
 // uploaded by pqh_batch_run_staged on the copy stream instead of synchronously (a slot's creation then
 // never waits behind the other slots' payload copies on the DMA engines)
 thread_local bool g_defer_tables = false;
+// set by create_codec_batch around pqh_batch_create: the payload is the image buffer the codec kernels
+// rebuild at the start of every run, so no chunk's values are taken from it in place
+thread_local bool g_codec_batch = false;
 
 // PQH_SNAPPY_PAGE=1 (A/B experiments): device SNAPPY by k_snappy, one workgroup per page, instead of
 // the multi-workgroup pipeline (k_snap_spec / stitch / emit / fixup).
@@ -141,6 +144,14 @@ bool snappy_page_mode() {
 // (k_ba_wspec / wstitch / wcopy) instead of the fused k_ba_chain.
 bool fuse_enabled() {
   const char* f = getenv("PQH_BA_FUSE");
+  return !(f && f[0] == '0');
+}
+
+// PQH_PLAIN_ALIAS=0 (A/B profiling, tests): required fixed-width PLAIN chunks whose page images stand
+// back to back are copied into a values buffer (TK_COPY tiles) like every other PLAIN chunk, instead
+// of being handed out where they stand in the payload.
+bool plain_alias_enabled() {
+  const char* f = getenv("PQH_PLAIN_ALIAS");
   return !(f && f[0] == '0');
 }
 
@@ -260,57 +271,6 @@ std::shared_ptr<uint8_t> pinned_acquire(pqh_ctx* ctx, size_t bytes) {
   });
 }
 
-int32_t resolve_kind(int32_t type, int32_t type_length, int32_t enc, int32_t* vs) {
-  if (enc == PQH_ENC_PLAIN_DICTIONARY) enc = PQH_ENC_RLE_DICTIONARY;
-  int32_t size = 0;
-  switch (type) {
-    case PQH_BOOLEAN: size = 1; break;
-    case PQH_INT32: case PQH_FLOAT: size = 4; break;
-    case PQH_INT64: case PQH_DOUBLE: size = 8; break;
-    case PQH_INT96: size = 12; break;
-    case PQH_FIXED_LEN_BYTE_ARRAY: size = type_length > 0 ? type_length : 0; break;
-    default: size = 0;
-  }
-  *vs = size;
-  switch (type) {
-    case PQH_BOOLEAN:
-      if (enc == PQH_ENC_PLAIN) return K_PLAIN_BOOL;
-      if (enc == PQH_ENC_RLE) return K_RLE_BOOL;
-      return K_UNSUPPORTED;
-    case PQH_BYTE_ARRAY:
-      if (enc == PQH_ENC_PLAIN) return K_PLAIN_BA;
-      if (enc == PQH_ENC_DELTA_LENGTH_BYTE_ARRAY) return K_DLBA;
-      if (enc == PQH_ENC_DELTA_BYTE_ARRAY) return K_DBA;
-      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
-      return K_UNSUPPORTED;
-    case PQH_FIXED_LEN_BYTE_ARRAY:
-      if (enc == PQH_ENC_PLAIN) return type_length > 0 ? K_PLAIN_FIXED : type_length == 0 ? K_PLAIN_BA : K_FLBA_NEGATIVE;
-      if (enc == PQH_ENC_DELTA_BYTE_ARRAY) {
-        *vs = 0;
-        return K_DBA;
-      }
-      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
-      return K_UNSUPPORTED;
-    case PQH_FLOAT:
-    case PQH_DOUBLE:
-      if (enc == PQH_ENC_PLAIN) return K_PLAIN_FIXED;
-      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
-      return K_UNSUPPORTED;
-    case PQH_INT96:
-      if (enc == PQH_ENC_PLAIN) return K_PLAIN_INT96;
-      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
-      return K_UNSUPPORTED;
-    case PQH_INT32:
-    case PQH_INT64:
-      if (enc == PQH_ENC_PLAIN) return K_PLAIN_FIXED;
-      if (enc == PQH_ENC_DELTA_BINARY_PACKED) return type == PQH_INT32 ? K_DELTA32 : K_DELTA64;
-      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
-      return K_UNSUPPORTED;
-    default:
-      return K_UNSUPPORTED;
-  }
-}
-
 // Chunks output as offsets + bytes: BYTE_ARRAY, and FIXED_LEN_BYTE_ARRAY without a fixed output
 // width (type_length <= 0, or DELTA_BYTE_ARRAY pages: the planner then sets value_size 0).
 bool is_ba_chunk(const DevChunk& D) {
@@ -325,6 +285,8 @@ struct pqh_batch {
   std::vector<pqh_page> pages;
   std::vector<DevPage> hpages;
   std::vector<DevChunk> hchunks;
+  std::vector<uint8_t> chunk_alias;  // 1: the chunk's values are its page images in the payload (no copy tiles)
+  int32_t plain_alias_chunks = 0;
   std::vector<Tile> expand_tiles;   // k_expand work list (kinds interleaved)
   int32_t expand_lev_n = 0;         // its first expand_lev_n tiles: the level tiles of the chunks with
                                     // nesting outputs, launched first (k_expand_lev) so that the
@@ -757,6 +719,8 @@ int pqh_batch_create(pqh_ctx* ctx, const pqh_chunk* chunks, int32_t num_chunks, 
   b->hpages.resize(size_t(num_pages));
   b->hchunks.resize(size_t(num_chunks));
   b->chunk_n.assign(size_t(num_chunks), 0);
+  b->chunk_alias.assign(size_t(num_chunks), 0);
+  const bool alias_on = plain_alias_enabled() && !g_codec_batch;
   b->k_read.assign(kNumKernels, 0);
   b->k_written.assign(kNumKernels, 0);
 
@@ -797,6 +761,24 @@ int pqh_batch_create(pqh_ctx* ctx, const pqh_chunk* chunks, int32_t num_chunks, 
       }
     if (flba_var) D.value_size = 0;
     const bool ba_chunk = is_ba_chunk(D);
+    // A required, non-repeated, fixed-width chunk of PLAIN data pages whose images hold exactly their
+    // values and stand back to back from a 64-byte aligned address: the payload already holds the
+    // chunk's values array, so it is handed out in place and k_expand gets no copy tiles for it.
+    // (k_prologue / k_scan still run over its pages: states, value bases and page results as ever.)
+    const int32_t avs = plain_value_size(C.column);
+    bool alias = alias_on && avs > 0 && C.host_status == PQH_OK && C.column.max_def == 0 && C.column.max_rep == 0 &&
+                 C.num_pages > 0 &&
+                 (reinterpret_cast<uintptr_t>(b->d_payload) + uintptr_t(pages[C.first_page].image_offset)) % 64 == 0;
+    for (int32_t i = 0; i < C.num_pages && alias; i++) {
+      const pqh_page& Q = pages[C.first_page + i];
+      alias = (Q.page_type == PQH_DATA_PAGE || Q.page_type == PQH_DATA_PAGE_V2) && Q.encoding == PQH_ENC_PLAIN &&
+              Q.num_values >= 0 && Q.def_levels_byte_length == 0 && Q.rep_levels_byte_length == 0 &&
+              Q.image_offset >= 0 && int64_t(Q.image_len) == int64_t(Q.num_values) * avs &&
+              Q.image_offset + Q.image_len <= payload_bytes &&
+              (i == 0 || Q.image_offset == pages[C.first_page + i - 1].image_offset + pages[C.first_page + i - 1].image_len);
+    }
+    b->chunk_alias[size_t(c)] = alias ? 1 : 0;
+    b->plain_alias_chunks += alias ? 1 : 0;
     D.batile_base = int32_t(b->ba_tiles.size());
     if (ba_chunk) b->ba_chunks.push_back(c);
     int64_t level_base = 0;
@@ -923,6 +905,7 @@ int pqh_batch_create(pqh_ctx* ctx, const pqh_chunk* chunks, int32_t num_chunks, 
       switch (kind) {
         case K_PLAIN_FIXED:
         case K_PLAIN_INT96: {
+          if (alias) break;  // the image is the output
           const int64_t ct = ceil_div(n * pvs, kCopyTileBytes);
           for (int32_t k = 0; k < ct; k++) by_kind[TK_COPY].push_back(Tile{p, k, TK_COPY, 1});
           break;
@@ -1139,8 +1122,12 @@ int pqh_batch_create(pqh_ctx* ctx, const pqh_chunk* chunks, int32_t num_chunks, 
     // values: fixed width, or the fixed-width pages' scratch of a FIXED_LEN_BYTE_ARRAY chunk laid out as byte arrays
     const int32_t vsz = D.value_size > 0 ? D.value_size : (ba_chunk && D.physical_type == PQH_FIXED_LEN_BYTE_ARRAY
                                                                 ? std::max(D.type_length, 0) : 0);
-    if ((rc = dalloc(b, &p, vsz == 0 && ba_chunk ? 64 : size_t(n) * size_t(std::max(vsz, 1)) + 64))) break;
-    D.values = static_cast<uint8_t*>(p);
+    if (b->chunk_alias[size_t(c)]) {  // in place: nothing allocated, nothing freed, never written through
+      D.values = const_cast<uint8_t*>(b->d_payload) + b->pages[size_t(D.first_page)].image_offset;
+    } else {
+      if ((rc = dalloc(b, &p, vsz == 0 && ba_chunk ? 64 : size_t(n) * size_t(std::max(vsz, 1)) + 64))) break;
+      D.values = static_cast<uint8_t*>(p);
+    }
     if (D.physical_type == PQH_INT96) {
       // the reference's nil values (type_int96.go:21-42): a PLAIN page may end with a short value
       // (known only once notNull is), a dictionary page's last entry may be short (known now)
@@ -1924,6 +1911,7 @@ int pqh_batch_sync(pqh_batch* b) {
     switch (P.kind) {
       case K_PLAIN_FIXED:
       case K_PLAIN_INT96:
+        if (b->chunk_alias[size_t(P.chunk)]) break;  // handed out in place: no kernel moves these bytes
         b->k_read[2] += vals;
         b->k_written[2] += vals;
         break;
@@ -2278,6 +2266,7 @@ int pqh_batch_path_info(const pqh_batch* b, pqh_batch_paths* out) {
   out->ba_fuse_active = b->ba_fuse_on ? 1 : 0;
   out->ba_fuse_fallbacks = b->ba_fuse_fallbacks;
   out->regrows = b->regrows;
+  out->plain_alias_chunks = b->plain_alias_chunks;
   out->graph_replay = (graphs_enabled() && !b->graph_failed && !flat_batch(b) &&
                        !(b->ctx->flags & (PQH_CTX_PROFILE | PQH_CTX_STREAMING))) ? 1 : 0;
   return PQH_OK;
@@ -2347,8 +2336,10 @@ int create_codec_batch(pqh_ctx* ctx, const pqh_host_batch* hb, void* d_src, pqh_
     dev_free(ctx, img);
     return set_err(ctx, PQH_ERR_HIP, std::string("image buffer: ") + hipGetErrorString(e));
   }
+  g_codec_batch = true;
   int rc = pqh_batch_create(ctx, hb->chunks.data(), int32_t(hb->chunks.size()), hb->pages.data(),
                             int32_t(hb->pages.size()), img, hb->image_bytes, out);
+  g_codec_batch = false;
   if (rc) {
     dev_free(ctx, img);
     return rc;

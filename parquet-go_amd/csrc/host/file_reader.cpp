@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "../kernels/decode.h"
 #include "codec.h"
 #include "internal.h"
 #include "thrift_compact.h"
@@ -86,6 +87,61 @@ struct pqh_file {
   // by default (compress.go:182-187), plus what RegisterBlockCompressor added (pqh_file_set_codecs)
   std::vector<int32_t> codecs{PQH_CODEC_UNCOMPRESSED, PQH_CODEC_GZIP, PQH_CODEC_SNAPPY, PQH_CODEC_ZSTD};
 };
+
+// getValuesDecoder (chunk_reader.go:106-159) resolved to a kernel kind (the walker asks whether a
+// V2 page has a decoder at all; the batch planner plans by the kind)
+namespace pqhip {
+int32_t resolve_kind(int32_t type, int32_t type_length, int32_t enc, int32_t* vs) {
+  if (enc == PQH_ENC_PLAIN_DICTIONARY) enc = PQH_ENC_RLE_DICTIONARY;
+  int32_t size = 0;
+  switch (type) {
+    case PQH_BOOLEAN: size = 1; break;
+    case PQH_INT32: case PQH_FLOAT: size = 4; break;
+    case PQH_INT64: case PQH_DOUBLE: size = 8; break;
+    case PQH_INT96: size = 12; break;
+    case PQH_FIXED_LEN_BYTE_ARRAY: size = type_length > 0 ? type_length : 0; break;
+    default: size = 0;
+  }
+  *vs = size;
+  switch (type) {
+    case PQH_BOOLEAN:
+      if (enc == PQH_ENC_PLAIN) return K_PLAIN_BOOL;
+      if (enc == PQH_ENC_RLE) return K_RLE_BOOL;
+      return K_UNSUPPORTED;
+    case PQH_BYTE_ARRAY:
+      if (enc == PQH_ENC_PLAIN) return K_PLAIN_BA;
+      if (enc == PQH_ENC_DELTA_LENGTH_BYTE_ARRAY) return K_DLBA;
+      if (enc == PQH_ENC_DELTA_BYTE_ARRAY) return K_DBA;
+      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
+      return K_UNSUPPORTED;
+    case PQH_FIXED_LEN_BYTE_ARRAY:
+      if (enc == PQH_ENC_PLAIN) return type_length > 0 ? K_PLAIN_FIXED : type_length == 0 ? K_PLAIN_BA : K_FLBA_NEGATIVE;
+      if (enc == PQH_ENC_DELTA_BYTE_ARRAY) {
+        *vs = 0;
+        return K_DBA;
+      }
+      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
+      return K_UNSUPPORTED;
+    case PQH_FLOAT:
+    case PQH_DOUBLE:
+      if (enc == PQH_ENC_PLAIN) return K_PLAIN_FIXED;
+      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
+      return K_UNSUPPORTED;
+    case PQH_INT96:
+      if (enc == PQH_ENC_PLAIN) return K_PLAIN_INT96;
+      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
+      return K_UNSUPPORTED;
+    case PQH_INT32:
+    case PQH_INT64:
+      if (enc == PQH_ENC_PLAIN) return K_PLAIN_FIXED;
+      if (enc == PQH_ENC_DELTA_BINARY_PACKED) return type == PQH_INT32 ? K_DELTA32 : K_DELTA64;
+      if (enc == PQH_ENC_RLE_DICTIONARY) return K_DICT;
+      return K_UNSUPPORTED;
+    default:
+      return K_UNSUPPORTED;
+  }
+}
+}  // namespace pqhip
 
 namespace {
 
@@ -310,7 +366,7 @@ struct ChunkPlan {
   pqh_chunk chunk;
   std::vector<PageOp> ops;
   int32_t codec = 0;
-  int64_t image = 0;      // image area bytes (64-aligned pages)
+  int64_t image = 0;      // image area bytes (64-aligned pages; a packed chunk: its pages back to back)
   int64_t src = 0;        // device codecs: source area bytes
   int64_t image_base = 0, src_base = 0;  // global offsets (assigned after planning)
   double seconds = 0;
@@ -490,7 +546,28 @@ void plan_chunk(const pqh_file* f, const ColumnMeta& col, const ChunkMeta& m, in
     }
     place();
   }
-  w.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  // A required, non-repeated, fixed-width chunk of PLAIN data pages only: every page image is its
+  // decoded values (no levels in front, little-endian at natural width), so with the images back to
+  // back the chunk's values array already stands in the payload and the batch can hand it out as
+  // it is (pqh_chunk_out.values, include/pqhip.h).  The first page keeps its 64-byte alignment.
+  // Every other chunk, and every chunk of a device-codec load, keeps 64-aligned pages.
+  const int32_t vsz = plain_value_size(col.col);
+  bool pack = !dev_codecs && vsz > 0 && max_def == 0 && max_rep == 0 && !have_dict && !w.ops.empty();
+  for (size_t i = 0; i < w.ops.size() && pack; i++) {
+    const pqh_page& pg = w.ops[i].pg;
+    pack = (pg.page_type == PQH_DATA_PAGE || pg.page_type == PQH_DATA_PAGE_V2) && pg.encoding == PQH_ENC_PLAIN &&
+           pg.num_values >= 0 && pg.def_levels_byte_length == 0 && pg.rep_levels_byte_length == 0 &&
+           int64_t(pg.image_len) == int64_t(pg.num_values) * vsz;
+  }
+  if (pack) {
+    int64_t at = 0;
+    for (PageOp& op : w.ops) {
+      op.pg.image_offset = at;
+      at += op.pg.image_len;
+    }
+    w.image = at;
+  }
+  w.seconds =std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // Materialise one planned page: host codecs -> its image at `img`; device codecs -> its source

@@ -100,7 +100,7 @@ class KernelStat(ctypes.Structure):
 
 class BatchPaths(ctypes.Structure):
     _fields_ = [("flat_active", i32), ("flat_fallbacks", i32), ("ba_fuse_active", i32), ("ba_fuse_fallbacks", i32),
-                ("regrows", i32), ("graph_replay", i32), ("reserved", i32 * 2)]
+                ("regrows", i32), ("graph_replay", i32), ("plain_alias_chunks", i32), ("reserved", i32)]
 
 
 # (name, restype, argtypes) for every function of include/pqhip.h
@@ -577,8 +577,9 @@ class Batch:
         return [arr[i] for i in range(n.value)]
 
     def paths(self):
-        """{flat_active, flat_fallbacks, ba_fuse_active, ba_fuse_fallbacks, regrows, graph_replay}:
-        the decode paths the batch takes now and the fallbacks pqh_batch_sync made."""
+        """{flat_active, flat_fallbacks, ba_fuse_active, ba_fuse_fallbacks, regrows, graph_replay,
+        plain_alias_chunks}: the decode paths the batch takes now, the fallbacks pqh_batch_sync made,
+        and the chunks whose values are handed out in place in the payload."""
         p = BatchPaths()
         self.ctx.check(self.L.pqh_batch_path_info(self.h, ctypes.byref(p)))
         return {k: getattr(p, k) for k, _ in BatchPaths._fields_ if k != "reserved"}
